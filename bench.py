@@ -7,10 +7,13 @@ one launch of the dual active-set kernel (csrc/zmp.hip) through the C-ABI (ccc_z
 plus -- for N > 1 GPUs -- the RCCL all-gather of the planned ZMPs (north_star).  Weak scaling: every rank
 solves its own batch of 65536 instances (seed = 20250928 + rank); value = all ranks' solves / max-over-ranks time.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--no-cpu-baseline] [--workload zmp|zmp100|xy|ddp|srb|ism|z|ddpzmp]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full [--no-cpu-baseline] ...]
+                  [--workload zmp|zmp100|xy|ddp|srb|ism|z|ddpzmp]
   N > 1:  python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
               --master-port P bench.py --gpus N --steps K --warmup W
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints value / ms_per_step; everything
+else the headline line can carry (status and pivot statistics, history legs, host-to-host p50, strong-scaling leg,
+roofline and counters, cpu_baseline and parity, the `secondary` workloads) is measured with --full.
 """
 import argparse
 import json
@@ -289,6 +292,15 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--batch", type=int, default=65536, help="instances per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="headline workload: beside the timed steps also measure and check everything else the line can carry "
+                         "(status / pivot statistics, `history`, host-to-host p50, `strong_scaling` for N > 1 GPUs, `roofline` "
+                         "with its counters, `cpu_baseline` and parity, `secondary`); the --no-* options below leave single "
+                         "parts of it out.  The lines of the other --workload values are not affected")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="headline workload: rank 0 writes what the last timed step computed to DIR/zmp.npy (float64 [batch, 2], "
+                         "its own planned ZMPs) and, for N > 1 GPUs, DIR/zmp_gathered.npy (the all-gathered ones); the inputs "
+                         "are seeded, so the same arguments give the same instances in every run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--ramp-steps", type=int, default=300,
                     help="untimed launches BEFORE the W warm-up steps (the same count on every rank): after the idle "
@@ -313,7 +325,7 @@ def main():
                     help="skip the second measurement on a handle without a history (profiling runs: one kind of launch)")
     ap.add_argument("--no-secondary", action="store_true",
                     help="headline only: skip the `secondary` entries (configs 3, 4, 5: xy 65536, ddp 4096, srb 32768, 20 timed "
-                         "steps each over rotating batches, each with roofline / cpu_baseline / parity) the default one-GPU command appends")
+                         "steps each over rotating batches, each with roofline / cpu_baseline / parity) the one-GPU command appends with --full")
     ap.add_argument("--workload", choices=["zmp", "zmp100", "xy", "ddp", "srb", "walk", "multi", "xywalk", "ism", "z", "ddpzmp"], default="zmp",
                     help="zmp (default) = the headline metric; the others measure the remaining classes with the same "
                          "protocol (bench_secondary.py)")
@@ -324,6 +336,8 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    if args.dump_outputs and args.workload != "zmp":
+        raise SystemExit("--dump-outputs writes the outputs of the headline workload only (--workload zmp)")
     if world != args.gpus:
         if world == 1 and args.gpus > 1:
             raise SystemExit("--gpus %d needs torch.distributed.run --nproc-per-node %d" % (args.gpus, args.gpus))
@@ -373,8 +387,13 @@ def main():
             full = fx.make_zmp_batch(args.batch, N, dt, 1.0, seed=20250928 + k)
             ring_host.append({kk: np.ascontiguousarray(v[lo:hi]) for kk, v in full.items()})
     else:
-        # RING distinct draws of the workload per rank (seed 20250928 + 8 rank + k), all resident in HBM
-        ring_host = [fx.make_zmp_batch(n, N, dt, 1.0, seed=20250928 + 8 * rank + k) for k in range(max(1, args.ring))]
+        # RING distinct draws of the workload per rank (seed 20250928 + 8 rank + k), all resident in HBM; drawn side by
+        # side to shorten the set-up (numpy releases the interpreter lock in the array operations that take the time)
+        from concurrent.futures import ThreadPoolExecutor
+
+        with ThreadPoolExecutor(max_workers=8) as pool:
+            ring_host = list(pool.map(lambda k: fx.make_zmp_batch(n, N, dt, 1.0, seed=20250928 + 8 * rank + k),
+                                      range(max(1, args.ring))))
     R = len(ring_host)
     batch = ring_host[0]
     ring = [(torch.from_numpy(b["x0"]).to(dev), torch.from_numpy(b["zlim"]).to(dev)) for b in ring_host]
@@ -409,9 +428,9 @@ def main():
                 pending[k].wait()
                 pending[k] = None
 
-    # one untimed launch per batch of the ring with the status array: pivot statistics / status check over all of them
+    # --full: one untimed launch per batch of the ring with the status array: pivot statistics / status check over all of them
     n_bad, piv_sum = 0, 0.0
-    for rx0, rzl in ring:
+    for rx0, rzl in ring if args.full else ():
         mpc.plan_batch_device(rx0, rzl, 0.005, zmp, None, status, stream)
         torch.cuda.synchronize(dev)
         st = status.cpu().numpy()
@@ -445,6 +464,12 @@ def main():
         elapsed = float(t.item())
     kern_ms = np.array([a.elapsed_time(b) for a, b in evs])  # HIP events on the launch stream
     timed_kernel = mpc.last_kernel()  # which kernel the timed launches ran: asked of the library (ccc_zmp_last_kernel)
+    if args.dump_outputs and rank == 0:
+        k = (counter[0] - 1) & 1  # the output buffer of the last timed step
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "zmp.npy"), zbuf[k].cpu().numpy())
+        if world > 1:
+            np.save(os.path.join(args.dump_outputs, "zmp_gathered.npy"), gathered[k].cpu().numpy())
     if os.environ.get("CCC_BENCH_DEBUG") and rank == 0:
         print("kern_ms", np.round(kern_ms[:24], 3).tolist(), "wall_ms", 1e3 * elapsed,
               "span_ms", evs[0][0].elapsed_time(evs[-1][1]), file=sys.stderr)
@@ -454,7 +479,7 @@ def main():
     # it).  Two more figures beside `value`: the same rotation on a handle that keeps no history at all
     # (CCC_ZMP_HISTORY=0, read at creation), and ONE batch repeated on a fresh handle -- the schedule's best case.
     no_hist = None
-    if world == 1 and not args.no_history_leg:
+    if args.full and world == 1 and not args.no_history_leg:
         def timed(h, rotate):
             for i in range(args.warmup + 20):
                 rx0, rzl = ring[i % R] if rotate else ring[0]
@@ -492,11 +517,12 @@ def main():
     # and writes the ZMPs in the caller's page-locked memory, no copy) and from pageable numpy arrays (staged chunk by
     # chunk through the handle's pinned buffers)
     h2h, h2h_pageable = [], []
-    px0 = torch.from_numpy(batch["x0"]).pin_memory()
-    pzl = torch.from_numpy(batch["zlim"]).pin_memory()
-    pz = torch.empty((n, 2), dtype=torch.float64).pin_memory()
-    pgath = torch.empty((world * n, 2), dtype=torch.float64).pin_memory() if world > 1 else None
-    n_h2h = 0 if args.no_host_p50 else 200
+    n_h2h = 200 if args.full and not args.no_host_p50 else 0
+    if n_h2h:
+        px0 = torch.from_numpy(batch["x0"]).pin_memory()
+        pzl = torch.from_numpy(batch["zlim"]).pin_memory()
+        pz = torch.empty((n, 2), dtype=torch.float64).pin_memory()
+        pgath = torch.empty((world * n, 2), dtype=torch.float64).pin_memory() if world > 1 else None
     for _ in range(20 if n_h2h else 0):
         mpc.plan_batch_pinned(px0, pzl, 0.005, pz)
     if world > 1:
@@ -510,10 +536,11 @@ def main():
             pgath.copy_(gathered[0], non_blocking=True)
             torch.cuda.synchronize(dev)
         h2h.append(1e3 * (time.perf_counter() - t1))
-    zref = torch.empty((n, 2), dtype=torch.float64, device=dev)  # batch 0 of the ring through the device entry
-    mpc.plan_batch_device(x0, zlim, 0.005, zref, None, None, stream)
-    torch.cuda.synchronize(dev)
-    assert not n_h2h or np.array_equal(pz.numpy(), zref.cpu().numpy()), "pinned path differs from the device path"
+    if args.full:  # (the answers of batch 0: what the pinned path above and the CPU baseline below are compared with)
+        zref = torch.empty((n, 2), dtype=torch.float64, device=dev)  # batch 0 of the ring through the device entry
+        mpc.plan_batch_device(x0, zlim, 0.005, zref, None, None, stream)
+        torch.cuda.synchronize(dev)
+        assert not n_h2h or np.array_equal(pz.numpy(), zref.cpu().numpy()), "pinned path differs from the device path"
     if rank == 0 and n_h2h:
         for _ in range(8):
             t1 = time.perf_counter()
@@ -521,7 +548,7 @@ def main():
             h2h_pageable.append(1e3 * (time.perf_counter() - t1))
         h2h_pageable = h2h_pageable[2:]
     p50_h2h = float(np.median(h2h)) if h2h else 0.0
-    if world > 1:
+    if world > 1 and n_h2h:
         t = torch.tensor([p50_h2h], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         p50_h2h = float(t.item())
@@ -529,7 +556,7 @@ def main():
     # weak-scaling runs on N > 1 GPUs also time BASELINE's literal configuration -- 65536 instances in TOTAL, contiguous
     # shards of batch / N per GPU -- so that one launch of the driver's command yields both curves
     strong = None
-    if world > 1 and args.scaling == "weak" and args.batch % world == 0:
+    if args.full and world > 1 and args.scaling == "weak" and args.batch % world == 0:
         ns = args.batch // world
         ring_s = [(a[:ns].contiguous(), b[:ns].contiguous()) for a, b in ring]  # rotating here too
         sz = [torch.empty((ns, 2), dtype=torch.float64, device=dev) for _ in range(2)]
@@ -569,21 +596,6 @@ def main():
     if rank == 0:
         ms_per_step = 1e3 * elapsed / args.steps
         value = world * n * args.steps / elapsed
-        kavg = float(kern_ms.mean()) * 1e-3
-        achieved = ALGO_BYTES_PER_SOLVE * n / kavg / 1e9
-        tflops = pivots_per_solve * FLOP_PER_PIVOT * n / kavg / 1e12
-        vc = valu_counters(n, timed_kernel)
-        traffic, traffic_src = measured_traffic(n, timed_kernel)
-        live = None
-        if world == 1 and not args.inner and not args.no_live_counters:
-            live, live_src = live_counters(n, timed_kernel)
-            if live is not None:
-                traffic = live["FETCH_SIZE"] * 1024 * 2 + live["WRITE_SIZE"] * 1024
-                traffic_src = live_src
-                vc = {"valu_insts_per_solve": live["SQ_INSTS_VALU"] / n,
-                      "valu_issue_frac": live["SQ_INSTS_VALU"] * 4.0 / (1024.0 * live["dispatch_ns"] * 2.4)}
-            else:
-                traffic_src = "%s; live collection: %s" % (traffic_src, live_src)
         out = {
             "metric": "LinearMpcZmp planOnce() solves/sec (N=32, fp64, inputs resident in HBM)",
             "value": value,
@@ -593,11 +605,7 @@ def main():
             "warmup": args.warmup,
             "ramp_steps": args.ramp_steps,  # untimed launches before the warm-up (GPU clock ramp), see --ramp-steps
             "ms_per_step": ms_per_step,
-            # SURVEY.md 8(d): median wall time from "inputs resident in pinned host memory" to "planned ZMPs back in pinned
-            # host memory on every rank" (max over ranks); PCIe-inclusive, never the `value` above
-            "p50_ms": p50_h2h if n_h2h else None,
             "p50_kernel_ms": float(np.median(kern_ms)),
-            "p50_pageable_host_ms": float(np.median(h2h_pageable)) if n_h2h else None,
             "higher_is_better": True,
             "scaling": args.scaling if world > 1 else "weak",
             "vs_baseline": None,
@@ -609,57 +617,77 @@ def main():
                                        if args.scaling == "strong" and world > 1 else "weak scaling", R),
                        "batch_per_gpu": n, "ring": R, "horizon_steps": N, "parallelism": "batch-sharded x%d" % world,
                        "collective": "all_gather(zmp)" if world > 1 else "none"},
+            "distributed": dinfo,
+        }
+        if args.full:
+            kavg = float(kern_ms.mean()) * 1e-3
+            achieved = ALGO_BYTES_PER_SOLVE * n / kavg / 1e9
+            tflops = pivots_per_solve * FLOP_PER_PIVOT * n / kavg / 1e12
+            vc = valu_counters(n, timed_kernel)
+            traffic, traffic_src = measured_traffic(n, timed_kernel)
+            live = None
+            if world == 1 and not args.inner and not args.no_live_counters:
+                live, live_src = live_counters(n, timed_kernel)
+                if live is not None:
+                    traffic = live["FETCH_SIZE"] * 1024 * 2 + live["WRITE_SIZE"] * 1024
+                    traffic_src = live_src
+                    vc = {"valu_insts_per_solve": live["SQ_INSTS_VALU"] / n,
+                          "valu_issue_frac": live["SQ_INSTS_VALU"] * 4.0 / (1024.0 * live["dispatch_ns"] * 2.4)}
+                else:
+                    traffic_src = "%s; live collection: %s" % (traffic_src, live_src)
+            # SURVEY.md 8(d): median wall time from "inputs resident in pinned host memory" to "planned ZMPs back in pinned
+            # host memory on every rank" (max over ranks); PCIe-inclusive, never the `value` above
+            out["p50_ms"] = p50_h2h if n_h2h else None
+            out["p50_pageable_host_ms"] = float(np.median(h2h_pageable)) if n_h2h else None
             # the bound that binds is VALU issue (fp64 vector pipe), not HBM and not MFMA: `achieved/peak/frac` are the
             # HBM figures the contract asks for, `valu` the ones that say how far the kernel is from ITS roofline
-            "roofline": {"bound": "valu", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         # (PMC counters need rocprofv3 around the process: collected by scripts/prof_zmp.sh -- this command
-                         #  under `--pmc FETCH_SIZE` / `--pmc WRITE_SIZE`, one pass each -- and read back from profiles/, only
-                         #  when that summary was made from the kernel sources this library was built from)
-                         "traffic_source": traffic_src,
-                         "algorithmic_bytes": ALGO_BYTES_PER_SOLVE * n,
-                         "kernel": timed_kernel,
-                         "kernel_avg_ms": kavg * 1e3,
-                         "kernel_avg_ms_what": "HIP events round the library call on its stream: the solve kernel plus, on a "
-                                               "handle with a history, the two order_by_count kernels (counting sort of the "
-                                               "last call's pivot counts) in front of it -- both in profiles/*_zmp_kernel_stats.csv",
-                         "valu": {"achieved": tflops, "peak": FP64_VECTOR_PEAK_TFLOPS, "unit": "TFLOP/s",
-                                  "frac": tflops / FP64_VECTOR_PEAK_TFLOPS,
-                                  "flop_per_solve": pivots_per_solve * FLOP_PER_PIVOT,
-                                  "issue_frac": vc["valu_issue_frac"] if vc else None,
-                                  "insts_per_pivot_trip": vc["valu_insts_per_solve"] / (0.5 * pivots_per_solve) if vc else None,
-                                  "what": "useful fp64 flop = pivots x 2048 (rank-1 update of the 32 x 32 tableau) over "
-                                          "the kernel time, against the vector-fp64 peak; issue_frac = VALU wave-"
-                                          "instructions x 4 clk / (SIMDs x clk) from the PMC pass in profiles/"},
-                         "mfma": {"utilisation": 0.0, "measured": "SQ_INSTS_MFMA = 0, SQ_VALU_MFMA_BUSY_CYCLES = 0 per launch "
-                                                                      "(profiles/r02_zmp_mfma_counters.csv)",
-                                  "why": "the pivot is a rank-1 update of a register-resident 32 x 32 tableau whose pivot "
-                                         "row and column depend on the previous pivot: no GEMM-shaped work to tile "
-                                         "(the smallest fp64 MFMA, 4x4x4, would run at 1/4 fill on a rank-1 product)"},
-                         "note": "algorithmic bytes = 1088 B/solve x batch: 1 % of HBM, the path is not memory-bound "
-                                 "(DESIGN.md section 4)"},
-            "pivots_per_solve": pivots_per_solve,
-            "unsolved": n_bad,
-        }
-        if live is not None:
-            out["roofline"]["live_counters"] = {k: live[k] for k in sorted(live)}
-            out["roofline"]["live_counters"]["what"] = (
-                "per dispatch of the headline kernel, averaged over the dispatches of the inner runs; dispatch_ns = the "
-                "kernel's duration under counter collection (SQ pass), the clock issue_frac is computed with")
-        if no_hist is not None:
-            out["history"] = no_hist
-        out["distributed"] = dinfo
-        if strong is not None:
-            out["strong_scaling"] = strong
-        if not args.no_cpu_baseline and world == 1:  # reported at N=1 only (the other ranks would idle meanwhile)
-            cb, ref_zmp, n_chk = cpu_baseline(batch)
-            out["cpu_baseline"] = cb
-            out["parity_max_abs_err"] = float(np.abs(zref.cpu().numpy()[:n_chk] - ref_zmp).max())
-    # configs 3, 4, 5 in the driver's record: the default one-GPU command also times LinearMpcXY
+            out["roofline"] = {"bound": "valu", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                               # (PMC counters need rocprofv3 around the process: collected by scripts/prof_zmp.sh -- this command
+                               #  under `--pmc FETCH_SIZE` / `--pmc WRITE_SIZE`, one pass each -- and read back from profiles/, only
+                               #  when that summary was made from the kernel sources this library was built from)
+                               "traffic_source": traffic_src,
+                               "algorithmic_bytes": ALGO_BYTES_PER_SOLVE * n,
+                               "kernel": timed_kernel,
+                               "kernel_avg_ms": kavg * 1e3,
+                               "kernel_avg_ms_what": "HIP events round the library call on its stream: the solve kernel plus, on a "
+                                                     "handle with a history, the two order_by_count kernels (counting sort of the "
+                                                     "last call's pivot counts) in front of it -- both in profiles/*_zmp_kernel_stats.csv",
+                               "valu": {"achieved": tflops, "peak": FP64_VECTOR_PEAK_TFLOPS, "unit": "TFLOP/s",
+                                        "frac": tflops / FP64_VECTOR_PEAK_TFLOPS,
+                                        "flop_per_solve": pivots_per_solve * FLOP_PER_PIVOT,
+                                        "issue_frac": vc["valu_issue_frac"] if vc else None,
+                                        "insts_per_pivot_trip": vc["valu_insts_per_solve"] / (0.5 * pivots_per_solve) if vc else None,
+                                        "what": "useful fp64 flop = pivots x 2048 (rank-1 update of the 32 x 32 tableau) over "
+                                                "the kernel time, against the vector-fp64 peak; issue_frac = VALU wave-"
+                                                "instructions x 4 clk / (SIMDs x clk) from the PMC pass in profiles/"},
+                               "mfma": {"utilisation": 0.0, "measured": "SQ_INSTS_MFMA = 0, SQ_VALU_MFMA_BUSY_CYCLES = 0 per launch "
+                                                                            "(profiles/r02_zmp_mfma_counters.csv)",
+                                        "why": "the pivot is a rank-1 update of a register-resident 32 x 32 tableau whose pivot "
+                                               "row and column depend on the previous pivot: no GEMM-shaped work to tile "
+                                               "(the smallest fp64 MFMA, 4x4x4, would run at 1/4 fill on a rank-1 product)"},
+                               "note": "algorithmic bytes = 1088 B/solve x batch: 1 % of HBM, the path is not memory-bound "
+                                       "(DESIGN.md section 4)"}
+            out["pivots_per_solve"] = pivots_per_solve
+            out["unsolved"] = n_bad
+            if live is not None:
+                out["roofline"]["live_counters"] = {k: live[k] for k in sorted(live)}
+                out["roofline"]["live_counters"]["what"] = (
+                    "per dispatch of the headline kernel, averaged over the dispatches of the inner runs; dispatch_ns = the "
+                    "kernel's duration under counter collection (SQ pass), the clock issue_frac is computed with")
+            if no_hist is not None:
+                out["history"] = no_hist
+            if strong is not None:
+                out["strong_scaling"] = strong
+            if not args.no_cpu_baseline and world == 1:  # reported at N=1 only (the other ranks would idle meanwhile)
+                cb, ref_zmp, n_chk = cpu_baseline(batch)
+                out["cpu_baseline"] = cb
+                out["parity_max_abs_err"] = float(np.abs(zref.cpu().numpy()[:n_chk] - ref_zmp).max())
+    # configs 3, 4, 5 in the driver's record: the one-GPU command with --full also times LinearMpcXY
     # (config 4), DdpCentroidal (config 3) and DdpSingleRigidBody (config 5's shape) with the same protocol and appends their
     # lines -- value, ms_per_step, steps, roofline (traffic + traffic_source), cpu_baseline (value_1thread), parity
     secondary = None
-    if world == 1 and not args.no_secondary and not args.batch_given:
+    if args.full and world == 1 and not args.no_secondary and not args.batch_given:
         import bench_secondary
 
         torch.cuda.empty_cache()

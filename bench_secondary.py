@@ -538,7 +538,7 @@ def live_secondary(workload, n, kernel):
 def measure(workload, n, steps, warmup, rank, world, local_rank, dist, strong=False, cpu=True, dinfo=None, history_leg=True,
             live=False):
     """One bench line (a dict; None on ranks other than 0) of a secondary workload: `warmup` untimed steps, `steps` timed
-    ones bracketed by barrier + synchronize, max over ranks.  Also what bench.py's default command appends to the headline
+    ones bracketed by barrier + synchronize, max over ranks.  Also what bench.py's --full command appends to the headline
     line as `secondary` (configs 3, 4, 5: VERDICT r4 item 2)."""
     dev = torch.device("cuda", local_rank)
     make = dict(zmp100=_zmp100, xy=_xy, xywalk=lambda a, b, c: _xy(a, b, c, True), ism=_ism, z=_z, ddpzmp=_ddpzmp, ddp=lambda a, b, c: _ddp(a, b, c, False), srb=lambda a, b, c: _ddp(a, b, c, True),

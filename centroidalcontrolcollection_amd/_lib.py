@@ -98,6 +98,14 @@ ABI_SYMBOLS = [
     "ccc_ddpzmp_plan_batch",
     "ccc_ddpzmp_closed_loop_device",
     "ccc_total_wrench_device",
+    "ccc_wrench_dist_default_config",
+    "ccc_wrench_distribution_device",
+    "ccc_pcc_create",
+    "ccc_pcc_destroy",
+    "ccc_pcc_horizon_steps",
+    "ccc_pcc_get_gains",
+    "ccc_pcc_plan_batch_device",
+    "ccc_pcc_plan_batch",
 ]
 
 

@@ -28,6 +28,9 @@ def host_fma_flags():
     except OSError:
         return []
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-function"]
+# units compiled with flags of their own on top of FLAGS (new units keep the compiler from forming packed fp32 operations;
+# the flags of the older units are part of their profiles' hashes and stay what they were)
+UNIT_FLAGS = {"wrench_dist.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 HASH_PATH = LIB_PATH + ".srchash"
@@ -41,7 +44,7 @@ def source_hash():
     """sha256 over everything the library is compiled from (file names + contents) and the compiler flags."""
     import hashlib
 
-    h = hashlib.sha256(" ".join(FLAGS).encode())
+    h = hashlib.sha256((" ".join(FLAGS) + repr(sorted(UNIT_FLAGS.items()))).encode())
     # (csrc/ includes ../../include/ccc_amd.h; a package installed without the include/ directory hashes csrc/ alone)
     deps = sources() + sorted(glob.glob(os.path.join(CSRC, "*.h"))) + sorted(glob.glob(os.path.join(CSRC, "*.inc"))) + sorted(
         glob.glob(os.path.join(_HERE, "..", "include", "*.h")))
@@ -122,7 +125,7 @@ def build_lib(force=False, verbose=False):
 
             def compile_one(src):
                 obj = os.path.join(obj_dir, os.path.splitext(os.path.basename(src))[0] + ".o")
-                cmd = [HIPCC] + cflags + ["-c", src, "-o", obj]
+                cmd = [HIPCC] + cflags + UNIT_FLAGS.get(os.path.basename(src), []) + ["-c", src, "-o", obj]
                 if verbose:
                     print(" ".join(cmd))
                 subprocess.check_call(cmd)

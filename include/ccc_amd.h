@@ -501,6 +501,77 @@ int ccc_total_wrench_device(int64_t n, int max_ridges, const int32_t * dim, cons
                             const double * scales, int scale_stride, const double * origin, double * wrench,
                             void * stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * ForceColl::WrenchDistribution::run (external dependency; the last line of CCC::PreviewControlCentroidal::planOnce,
+ * src/PreviewControlCentroidal.cpp:127-129) -- csrc/wrench_dist.hip, csrc/wrench_dist.h.  The second consumer of a
+ * planned wrench: it is projected onto the ridge forces of the current contact list.  ForceColl is not part of the
+ * reference tree, so the problem is stated here.  Per instance, with m = dim[k] ridges:
+ *   G (6 x m): column r = [(vertex_r - origin) x ridge_r; ridge_r]               (sva order: moment, then force)
+ *   minimise over s   1/2 (G s - w)' diag(wrench_weight) (G s - w) + 1/2 regular_weight s's
+ *   subject to        ridge_force_min <= s_r <= ridge_force_max
+ *   result: s and the projected wrench G s.   m = 0: the zero wrench (the reference's early return).
+ * The defaults below are ForceColl's WrenchDistribution::Configuration values AS RECALLED, not read from its sources
+ * (they are not on hand): wrench_weight all ones, regular_weight 1e-8, ridge_force_minmax (3, 1000).
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct
+{
+  double wrench_weight[6]; /* [moment; force], each > 0 */
+  double regular_weight;   /* > 0 */
+  double ridge_force_min, ridge_force_max;
+} ccc_wrench_dist_config_t;
+void ccc_wrench_dist_default_config(ccc_wrench_dist_config_t * cfg);
+
+/* n wrench distributions on the flattened contact arrays of ccc_total_wrench_device:
+ *   dim [n] i32, vertex / ridge [n][max_ridges][3] f64    max_ridges = 16, 32 or 64 (else CCC_ERR_UNSUPPORTED)
+ *   desired_wrench [n][6]  f64  [moment; force] about origin        origin [n][3]  f64
+ *   cfg                         NULL = the defaults
+ *   wrench_out [n][6]      f64  the projected wrench G s
+ *   scales_out [n][max_ridges]  f64  optional: the ridge forces s (0 beyond dim)
+ *   status     [n]         i32  optional: (iterations << 8) | CCC_STATUS_SOLVED / CCC_STATUS_MAX_ITER.  SOLVED is a
+ *                               certificate checked on the returned point (bounds, multiplier signs, stationarity).
+ * Device pointers + a HIP stream (asynchronous, no workspace: graph-capturable). */
+int ccc_wrench_distribution_device(int64_t n, int max_ridges, const int32_t * dim, const double * vertex,
+                                   const double * ridge, const double * desired_wrench, const double * origin,
+                                   const ccc_wrench_dist_config_t * cfg, double * wrench_out, double * scales_out,
+                                   int32_t * status, void * stream);
+
+/* ============================================================================================
+ * CCC::PreviewControlCentroidal   (/root/reference/include/CCC/PreviewControlCentroidal.h:137-262)
+ * Six one-dimensional preview controllers (jerk input; outputs position and wrench) and the wrench distribution.
+ * ============================================================================================ */
+typedef struct ccc_pcc ccc_pcc_t;
+#define CCC_PCC_MAX_STEPS 512 /* horizon steps whose gains (6 x 2N doubles) fit the kernel's LDS stage */
+
+/* Replaces PreviewControlCentroidal::PreviewControlCentroidal(mass, moment_of_inertia, horizon_duration, horizon_dt,
+ * weight_param) (src/PreviewControlCentroidal.cpp:74-89); horizon steps = ceil(horizon_duration / horizon_dt)
+ * (PreviewControl.h:71).  weight_pos / weight_wrench / weight_jerk [6] ([angular; linear]) or NULL for the defaults of
+ * PreviewControlCentroidal.h:204-209; cfg NULL = the wrench-distribution defaults.  The gains are computed here, on the
+ * host (PreviewControl.h:93-171). */
+int ccc_pcc_create(double mass, const double * moment_of_inertia, double horizon_duration, double horizon_dt,
+                   const double * weight_pos, const double * weight_wrench, const double * weight_jerk,
+                   const ccc_wrench_dist_config_t * cfg, int max_ridges, int device, ccc_pcc_t ** out);
+void ccc_pcc_destroy(ccc_pcc_t * h);
+int ccc_pcc_horizon_steps(const ccc_pcc_t * h);
+/* K [6][3], F [6][2N], riccati_error [6] (PreviewControl::K_, F_, riccati_error_ of the six axes); each may be NULL */
+int ccc_pcc_get_gains(const ccc_pcc_t * h, double * K, double * F, double * riccati_error);
+
+/* Replaces n calls of PreviewControlCentroidal::planOnce(motion_param, ref_data_func, initial_param, current_time,
+ * control_dt) (src/PreviewControlCentroidal.cpp:91-130), ref_data_func already sampled:
+ *   x0      [n][18]     f64  InitialParam: pos.vector(), vel.vector(), acc.vector() (each angular, then linear)
+ *   ref     [n][N][12]  f64  RefData::pos.vector(), RefData::wrench.vector() at current_time + (i + 1) horizon_dt
+ *   dim, vertex, ridge       motion_param.contact_list flattened (max_ridges of the handle)
+ *   control_dt               < 0: horizon_dt
+ *   wrench          [n][6]   f64  the return value (projected about initial_param.pos.linear())
+ *   planned_wrench  [n][6]   f64  optional: the wrench before projection
+ *   scales [n][max_ridges], status [n]: optional, as ccc_wrench_distribution_device
+ * _device: device pointers + a HIP stream (asynchronous); the other entry stages host arrays through the device. */
+int ccc_pcc_plan_batch_device(ccc_pcc_t * h, int64_t n, const double * x0, const double * ref, const int32_t * dim,
+                              const double * vertex, const double * ridge, double control_dt, double * wrench,
+                              double * planned_wrench, double * scales, int32_t * status, void * stream);
+int ccc_pcc_plan_batch(ccc_pcc_t * h, int64_t n, const double * x0, const double * ref, const int32_t * dim,
+                       const double * vertex, const double * ridge, double control_dt, double * wrench,
+                       double * planned_wrench, double * scales, int32_t * status);
+
 /* =========================================================================================
  * The closed-loop tests of the force-scale planners on the device -- csrc/centroidal_loop.hip:
  *   plan -> ForceColl::calcTotalWrench about the CoM -> CentroidalSim::update (+ addDisturb) -> plan ...

@@ -523,6 +523,8 @@ void ccc_wrench_dist_default_config(ccc_wrench_dist_config_t * cfg);
 
 /* n wrench distributions on the flattened contact arrays of ccc_total_wrench_device:
  *   dim [n] i32, vertex / ridge [n][max_ridges][3] f64    max_ridges = 16, 32 or 64 (else CCC_ERR_UNSUPPORTED)
+ *                               dim[k] is clamped to [0, max_ridges] (here and in ccc_pcc_plan_batch*); the slots at and
+ *                               beyond it are not read
  *   desired_wrench [n][6]  f64  [moment; force] about origin        origin [n][3]  f64
  *   cfg                         NULL = the defaults
  *   wrench_out [n][6]      f64  the projected wrench G s

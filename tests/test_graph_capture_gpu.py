@@ -1,4 +1,4 @@
-"""hipGraph capture of the *_plan_batch_device calls: everything a call enqueues (counter resets, the kernels, the fork
+"""hipGraph capture of the *_plan_batch_device calls and of ccc_wrench_distribution_device: everything a call enqueues (counter resets, the kernels, the fork
 to / join from the second stream of LinearMpcXY) is capturable once the handle's workspace exists (one eager call first:
 the workspace allocation is synchronous).  The replayed graph must give, bit for bit, what the eager call gives -- also
 after the inputs were overwritten in place, which is how a control loop uses it."""
@@ -210,6 +210,83 @@ def test_ddp_classes_graph_replay():
         g.replay()
         torch.cuda.synchronize()
         assert np.array_equal(out.cpu().numpy(), c.planOnceBatch(prob, x)["u"])
+
+
+def test_wrench_distribution_graph_replay():
+    """ccc_wrench_distribution_device: one kernel, no workspace.  The outputs the wrapper allocates during the capture
+    belong to the graph; each replay fills them again."""
+    import torch
+    from wrench_dist_ref import N_INST, make_batch
+
+    from centroidalcontrolcollection_amd import wrench as wmod
+
+    dev = torch.device("cuda:0")
+    M = 16
+    a = make_batch(M, M, seed=1)
+    b = make_batch(M, np.resize(np.array([16, 7, 0, 12, 3], np.int32), N_INST), seed=2)
+    t = [torch.from_numpy(np.ascontiguousarray(v)).to(dev) for v in a]  # dims, vertex, ridge, origin, w
+    cfg = wmod.WrenchDistConfig()
+    held = {}
+
+    def launch(s):
+        held["out"] = wmod.wrench_distribution_device(t[0], t[1], t[2], t[4], t[3], cfg, stream=s)
+
+    g = _capture(launch)
+    for batch in (b, a):
+        for dst, src in zip(t, batch):
+            dst.copy_(torch.from_numpy(np.ascontiguousarray(src)))
+        for out in held["out"]:
+            out.fill_(-1)
+        g.replay()
+        torch.cuda.synchronize()
+        eager = wmod.wrench_distribution_device(t[0], t[1], t[2], t[4], t[3], cfg)
+        torch.cuda.synchronize()
+        for got, want in zip(held["out"], eager):
+            assert torch.equal(got, want)
+        assert np.all((eager[2].cpu().numpy() & 0xff) == 0)
+
+
+def test_pcc_graph_replay():
+    """ccc_pcc_plan_batch_device: the fused kernel alone (the gains were staged at create)."""
+    import torch
+    from wrench_dist_ref import INERTIA, MASS, N_INST, make_batch
+
+    from centroidalcontrolcollection_amd import PreviewControlCentroidal
+
+    dev = torch.device("cuda:0")
+    n, N, M = N_INST, 5, 16
+    pc = PreviewControlCentroidal(MASS, INERTIA, N * 0.01, 0.01, max_ridges=M)
+
+    def inputs(seed):
+        dims, vertex, ridge, origin, _ = make_batch(M, M, seed=seed)
+        rng = np.random.default_rng(seed)
+        x0 = 0.05 * rng.standard_normal((n, 18))
+        x0[:, 3:6] = origin
+        ref = np.zeros((n, N, 12))
+        ref[:, :, 0:6] = 0.02 * rng.standard_normal((n, N, 6))
+        ref[:, :, 3:6] += origin[:, None, :]
+        ref[:, :, 6:12] = 5.0 * rng.standard_normal((n, N, 6))
+        return dict(x0=x0, ref=ref, dims=dims, vertex=vertex, ridge=ridge)
+
+    a, b = inputs(1), inputs(2)
+    t = {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in a.items()}
+    out = dict(wrench=torch.zeros((n, 6), dtype=torch.float64, device=dev),
+               planned_wrench=torch.zeros((n, 6), dtype=torch.float64, device=dev),
+               scales=torch.zeros((n, M), dtype=torch.float64, device=dev),
+               status_raw=torch.zeros(n, dtype=torch.int32, device=dev))
+    g = _capture(lambda s: pc.plan_batch_device(t["x0"], t["ref"], t["dims"], t["vertex"], t["ridge"], out["wrench"], 0.005,
+                                                out["planned_wrench"], out["scales"], out["status_raw"], stream=s))
+    for batch in (b, a):
+        for k in t:
+            t[k].copy_(torch.from_numpy(np.ascontiguousarray(batch[k])))
+        for v in out.values():
+            v.fill_(-1)
+        g.replay()
+        torch.cuda.synchronize()
+        eager = pc.planOnceBatch(batch["x0"], batch["ref"], batch["dims"], batch["vertex"], batch["ridge"], control_dt=0.005)
+        for k in out:
+            assert np.array_equal(out[k].cpu().numpy(), eager[k]), k
+        assert np.all(eager["status"] == 0)
 
 
 def test_workspace_growth_inside_a_capture_is_refused():

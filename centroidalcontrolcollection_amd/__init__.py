@@ -11,6 +11,7 @@ from .linear_mpc_z import LinearMpcZ  # noqa: F401
 from .ddp_zmp import DdpZmp  # noqa: F401
 from .linear_mpc_zmp import InitialParam, LinearMpcZmp, RefData  # noqa: F401
 from .preview_control_centroidal import PreviewControlCentroidal  # noqa: F401
+from .step_mpc import StepMpc  # noqa: F401
 
 __all__ = ["LinearMpcZmp", "RefData", "InitialParam", "DdpCentroidal", "DdpSingleRigidBody", "LinearMpcXY",
-           "IntrinsicallyStableMpc", "LinearMpcZ", "DdpZmp", "PreviewControlCentroidal"]
+           "IntrinsicallyStableMpc", "LinearMpcZ", "DdpZmp", "PreviewControlCentroidal", "StepMpc"]

@@ -106,6 +106,10 @@ ABI_SYMBOLS = [
     "ccc_pcc_get_gains",
     "ccc_pcc_plan_batch_device",
     "ccc_pcc_plan_batch",
+    "ccc_step_create",
+    "ccc_step_destroy",
+    "ccc_step_plan_batch_device",
+    "ccc_step_plan_batch",
 ]
 
 

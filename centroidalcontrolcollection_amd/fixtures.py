@@ -141,6 +141,25 @@ class FootstepManager:
         lim = self.zmpLimits(t)
         return RefData(lim[0], lim[1])
 
+    def makeStepMpcRefData(self, current_time):
+        # :385-448: a list of elements (is_single_support, zmp [2], end_time) up to 3 s ahead
+        current_time = current_time - 1e-6
+        elements = []
+        if not self.footstep_list_:
+            return [(False, _mid_pos(self.footstance_), current_time + 0.2)]
+        tmp = {k: v.copy() for k, v in self.footstance_.items()}
+        if current_time < self.footstep_list_[0].swing_start_time:
+            elements.append((False, _mid_pos(tmp), self.footstep_list_[0].swing_start_time))
+        for i, fs in enumerate(self.footstep_list_):
+            if i > 0 or current_time < fs.swing_end_time:
+                elements.append((True, tmp[opposite(fs.foot)].copy(), fs.swing_end_time))
+                tmp[fs.foot] = fs.pos.copy()
+            last = i == len(self.footstep_list_) - 1
+            elements.append((False, _mid_pos(tmp), fs.transit_end_time if last else self.footstep_list_[i + 1].swing_start_time))
+            if elements[-1][2] > current_time + 3.0:
+                break
+        return elements
+
 
 class ComZmpSim2d:
     """SimModels.h:76-137 with the 1-D model of :11-41, ZOH-discretised exactly:
@@ -272,6 +291,37 @@ def run_closed_loop(plan_once, com_height=1.0, sim_dt=0.005, end_time=10.0, dist
                 break
     lim = fm.zmpLimits(t)
     return log, dict(t=t, com=sim.pos(), zmp=planned, zmin=lim[0], zmax=lim[1])
+
+
+def run_closed_loop_step_mpc(plan_once, com_height=1.0, sim_dt=0.005, end_time=10.0, disturb_times=(4.5, 8.5),
+                             disturb=(0.05, 0.05)):
+    """The control loop of TestStepMpc.cpp:55-116 around any
+    `plan_once(ref_data, (pos [2], vel [2]), t) -> (current_zmp [2], next_foot_zmp [2] or None)`, with the footstep
+    update 0.1 s before the swing ends (:99-115).  Returns per-cycle records (t, com, zmp, ref_zmp) and the final state
+    for the assertions of :83,:119-122."""
+    fm = FootstepManager()
+    for fs in reference_scenario_footsteps():
+        fm.appendFootstep(fs)
+    sim = ComZmpSim2d(com_height, sim_dt)
+    planned = np.zeros(2)
+    t = 0.0
+    log = []
+    while t < end_time:
+        fm.update(t)
+        planned, next_foot = plan_once(fm.makeStepMpcRefData(t), (sim.pos(), sim.vel()), t)
+        planned = np.asarray(planned, np.float64).copy()
+        log.append(dict(t=t, com=sim.pos(), zmp=planned.copy(), ref_zmp=fm.refZmp(t)))
+        t += sim_dt
+        sim.update(planned)
+        for dtm in disturb_times:
+            if dtm <= t < dtm + sim_dt:
+                sim.addDisturb(disturb)
+                break
+        if fm.footstep_list_:
+            pre = fm.footstep_list_[0].swing_end_time - 0.1
+            if pre <= t < pre + sim_dt and next_foot is not None:
+                fm.footstep_list_[0].pos = np.asarray(next_foot, np.float64).copy()
+    return log, dict(t=t, com=sim.pos(), vel=sim.vel(), zmp=planned, ref_zmp=fm.refZmp(t))
 
 
 def run_closed_loop_ism(plan_once, com_height=1.0, sim_dt=0.005, end_time=10.0, disturb_times=(4.5, 8.5),

@@ -574,6 +574,52 @@ int ccc_pcc_plan_batch(ccc_pcc_t * h, int64_t n, const double * x0, const double
                        const double * vertex, const double * ridge, double control_dt, double * wrench,
                        double * planned_wrench, double * scales, int32_t * status);
 
+/* ============================================================================================
+ * CCC::StepMpc   (/root/reference/include/CCC/StepMpc.h:163-240, src/StepMpc.cpp:26-247) -- csrc/step_mpc.hip
+ * Footstep-adapting MPC on the step-to-step dynamics of the linear inverted pendulum: an unconstrained linear
+ * least-squares problem in the piecewise-constant ZMPs of up to CCC_STEP_MAX_ELEMENTS support phases.  The reference
+ * solves its normal equations; the kernel factors the stacked rows themselves by Givens rotations (the normal matrix
+ * squares a condition number that grows as e^(omega horizon)), both axes as two right-hand sides of one factorisation.
+ * ============================================================================================ */
+typedef struct ccc_step ccc_step_t;
+#define CCC_STEP_MAX_ELEMENTS 16
+#define CCC_STEP_HAS_NEXT_FOOT 0x100 /* status bit 8: next_foot_zmp holds a planned foothold (the reference's optional) */
+
+/* StepMpc1d::WeightParam (StepMpc.h:80-123; the defaults of :112-118 are 1e-2, 1, 1, 0, 0, 10, 10) */
+typedef struct
+{
+  double free_zmp, fixed_zmp, double_support, pos, vel, capture_point_abs, capture_point_rel;
+} ccc_step_weights_t;
+
+/* Replaces StepMpc::StepMpc(com_height, weight_param); weights NULL = the defaults.  CCC_ERR_INVALID_ARGUMENT, before
+ * the device is touched, for com_height <= 0, free_zmp <= 0 or fixed_zmp <= 0 (with a ZMP weight of zero the system can
+ * be rank deficient: the reference leans on column pivoting there, this library refuses) and for any negative weight.
+ * A weight of zero drops its rows, as the reference's `> 0.0` tests do. */
+int ccc_step_create(double com_height, const ccc_step_weights_t * weights, int device, ccc_step_t ** out);
+void ccc_step_destroy(ccc_step_t * h);
+
+/* Replaces n calls of StepMpc::planOnce(ref_data, initial_param, current_time):
+ *   num_elements      [n]         i32  ref_data.element_list.size(), 1 .. CCC_STEP_MAX_ELEMENTS
+ *   is_single_support [n][16]     i32  per element (entries at and beyond num_elements are not used)
+ *   end_time          [n][16]     f64
+ *   zmp               [n][16][2]  f64
+ *   x0                [n][4]      f64  InitialParam: pos x, y, vel x, y
+ *   current_time      [n]         f64
+ *   current_zmp       [n][2]      f64  PlannedData::current_zmp
+ *   next_foot_zmp     [n][2]      f64  PlannedData::next_foot_zmp: the ZMP of the first single-support element with index
+ *                                      >= 1; zero when there is none (CCC_STEP_HAS_NEXT_FOOT clear)
+ *   status            [n]         i32  optional: CCC_STATUS_SOLVED | CCC_STEP_HAS_NEXT_FOOT, or CCC_STATUS_INFEASIBLE with
+ *                                      NaN outputs for an instance with num_elements outside 1 .. 16, an element of
+ *                                      duration <= 0 or two consecutive double-support elements (StepMpc.h:186-187)
+ * _device: device pointers + a HIP stream (asynchronous, no workspace: graph-capturable); the other entry stages host
+ * arrays through the device. */
+int ccc_step_plan_batch_device(ccc_step_t * h, int64_t n, const int32_t * num_elements, const int32_t * is_single_support,
+                               const double * end_time, const double * zmp, const double * x0, const double * current_time,
+                               double * current_zmp, double * next_foot_zmp, int32_t * status, void * stream);
+int ccc_step_plan_batch(ccc_step_t * h, int64_t n, const int32_t * num_elements, const int32_t * is_single_support,
+                        const double * end_time, const double * zmp, const double * x0, const double * current_time,
+                        double * current_zmp, double * next_foot_zmp, int32_t * status);
+
 /* =========================================================================================
  * The closed-loop tests of the force-scale planners on the device -- csrc/centroidal_loop.hip:
  *   plan -> ForceColl::calcTotalWrench about the CoM -> CentroidalSim::update (+ addDisturb) -> plan ...

@@ -12,6 +12,9 @@ from .ddp_zmp import DdpZmp  # noqa: F401
 from .linear_mpc_zmp import InitialParam, LinearMpcZmp, RefData  # noqa: F401
 from .preview_control_centroidal import PreviewControlCentroidal  # noqa: F401
 from .step_mpc import StepMpc  # noqa: F401
+from .preview_control_zmp import PreviewControlZmp  # noqa: F401
+from .singular_preview_control_zmp import SingularPreviewControlZmp  # noqa: F401
 
 __all__ = ["LinearMpcZmp", "RefData", "InitialParam", "DdpCentroidal", "DdpSingleRigidBody", "LinearMpcXY",
-           "IntrinsicallyStableMpc", "LinearMpcZ", "DdpZmp", "PreviewControlCentroidal", "StepMpc"]
+           "IntrinsicallyStableMpc", "LinearMpcZ", "DdpZmp", "PreviewControlCentroidal", "StepMpc", "PreviewControlZmp",
+           "SingularPreviewControlZmp"]

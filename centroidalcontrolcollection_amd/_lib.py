@@ -110,6 +110,14 @@ ABI_SYMBOLS = [
     "ccc_step_destroy",
     "ccc_step_plan_batch_device",
     "ccc_step_plan_batch",
+    "ccc_pvz_create",
+    "ccc_pvz_destroy",
+    "ccc_pvz_horizon_steps",
+    "ccc_pvz_get_gains",
+    "ccc_pvz_plan_batch_device",
+    "ccc_pvz_plan_batch",
+    "ccc_pvz_plan_knots_batch_device",
+    "ccc_pvz_plan_knots_batch",
 ]
 
 

@@ -620,6 +620,67 @@ int ccc_step_plan_batch(ccc_step_t * h, int64_t n, const int32_t * num_elements,
                         const double * end_time, const double * zmp, const double * x0, const double * current_time,
                         double * current_zmp, double * next_foot_zmp, int32_t * status);
 
+/* ============================================================================================
+ * CCC::PreviewControlZmp   (/root/reference/include/CCC/PreviewControlZmp.h:92-140, src/PreviewControlZmp.cpp:15-76)
+ * CCC::SingularPreviewControlZmp   (include/CCC/SingularPreviewControlZmp.h:86-130, src/SingularPreviewControlZmp.cpp:7-88)
+ * -- csrc/preview_zmp.hip.  Both are, per axis, u = -K x + sum_{i<N} w_i r_i with r_i = ref_zmp_func(current_time +
+ * (i + off) horizon_dt) and a short epilogue; one handle type serves both, `kind` selects K, w, off and the epilogue:
+ *   CCC_PVZ_PREVIEW   off = 1, x = (CoM pos, vel, acc), u = CoM jerk; control_dt < 0 means horizon_dt
+ *   CCC_PVZ_SINGULAR  off = 0, x = (planned_zmp, CoM pos, vel), u = ZMP velocity; zmp = planned_zmp + control_dt u with
+ *                     control_dt AS PASSED (the reference's procOnce never substitutes horizon_dt, whatever its header says)
+ * The reference is either sampled by the caller (ref) or given as the knots of a piecewise-linear function, which is what
+ * FootstepManager::refZmp interpolates; the knot entry costs per knot, not per horizon step.
+ * ============================================================================================ */
+typedef struct ccc_pvz ccc_pvz_t;
+#define CCC_PVZ_PREVIEW 0
+#define CCC_PVZ_SINGULAR 1
+#define CCC_PVZ_MAX_STEPS 512 /* horizon steps: the weights of a lane fit its registers, the suffix tables 8.2 KB of LDS */
+#define CCC_PVZ_MAX_KNOTS 32
+
+/* Replaces PreviewControlZmp(com_height, horizon_duration, horizon_dt, weight_param) and SingularPreviewControlZmp(
+ * com_height, horizon_duration, horizon_dt); horizon steps N = ceil(horizon_duration / horizon_dt).  weight_zmp /
+ * weight_com_jerk: PREVIEW only, a value <= 0 means the default (1.0, 1e-8); ignored for SINGULAR.  K and w are computed
+ * here, on the host.  CCC_ERR_INVALID_ARGUMENT, before the device is touched, for an unknown kind, com_height <= 0,
+ * horizon_duration <= 0 or horizon_dt <= 0; CCC_ERR_UNSUPPORTED for N > CCC_PVZ_MAX_STEPS. */
+int ccc_pvz_create(int kind, double com_height, double horizon_duration, double horizon_dt, double weight_zmp,
+                   double weight_com_jerk, int device, ccc_pvz_t ** out);
+void ccc_pvz_destroy(ccc_pvz_t * h);
+int ccc_pvz_horizon_steps(const ccc_pvz_t * h);
+/* K [3], w [N] (PREVIEW: PreviewControl::K_, F_; SINGULAR: equation (16) and the recursion of :39-47 written as
+ * weights), riccati_error [1] (0 for SINGULAR); each may be NULL */
+int ccc_pvz_get_gains(const ccc_pvz_t * h, double * K, double * w, double * riccati_error);
+
+/* Replaces n calls of planOnce(ref_zmp_func, initial_param, current_time, control_dt), ref_zmp_func already sampled:
+ *   x0    [n][2][3]  f64  per axis, in the order of x above
+ *   ref   [n][2][N]  f64  per axis, ref_zmp_func(current_time + (i + off) horizon_dt)
+ *   zmp   [n][2]     f64  the return value
+ *   input [n][2]     f64  optional: u itself
+ * _device: device pointers + a HIP stream (asynchronous, no workspace: graph-capturable); the other entry stages host
+ * arrays through the device. */
+int ccc_pvz_plan_batch_device(ccc_pvz_t * h, int64_t n, const double * x0, const double * ref, double control_dt,
+                              double * zmp, double * input, void * stream);
+int ccc_pvz_plan_batch(ccc_pvz_t * h, int64_t n, const double * x0, const double * ref, double control_dt, double * zmp,
+                       double * input);
+
+/* The same with ref_zmp_func given as the linear interpolation of knots, as FootstepManager::refZmp reads ref_zmp_list_:
+ *   num_knots    [n]         i32  2 .. CCC_PVZ_MAX_KNOTS
+ *   knot_time    [n][32]     f64  strictly increasing over the first num_knots entries
+ *   knot_zmp     [n][32][2]  f64
+ *   current_time [n]         f64
+ *   status       [n]         i32  optional: CCC_STATUS_SOLVED or CCC_STATUS_INFEASIBLE
+ * Sample i lies in segment s iff knot_time[s] <= t_i < knot_time[s + 1], with t_i = current_time + (i + off) horizon_dt
+ * evaluated in double as written: the plan is that of the sampled entry on the samples this rule gives, whatever the
+ * rounding of t_i.  (The +1e-6 of FootstepManager::refZmp belongs to the caller: fold it into current_time.)  An
+ * instance with num_knots outside 2 .. 32, knot times that do not increase, or any sample outside [first knot, last
+ * knot) -- where the reference dereferences end() -- is flagged CCC_STATUS_INFEASIBLE and returns NaN, never an
+ * extrapolation. */
+int ccc_pvz_plan_knots_batch_device(ccc_pvz_t * h, int64_t n, const int32_t * num_knots, const double * knot_time,
+                                    const double * knot_zmp, const double * x0, const double * current_time,
+                                    double control_dt, double * zmp, double * input, int32_t * status, void * stream);
+int ccc_pvz_plan_knots_batch(ccc_pvz_t * h, int64_t n, const int32_t * num_knots, const double * knot_time,
+                             const double * knot_zmp, const double * x0, const double * current_time, double control_dt,
+                             double * zmp, double * input, int32_t * status);
+
 /* =========================================================================================
  * The closed-loop tests of the force-scale planners on the device -- csrc/centroidal_loop.hip:
  *   plan -> ForceColl::calcTotalWrench about the CoM -> CentroidalSim::update (+ addDisturb) -> plan ...

@@ -120,6 +120,23 @@ public:
     return out;
   }
 
+  /** \brief The control loop of tests/src/TestIntrinsicallyStableMpc.cpp:55-100 for n instances in one launch (new):
+      a thin forward to ccc_ism_closed_loop_device (ccc_amd.h), whose argument list and layouts it shares.  All pointers
+      are device pointers but disturb_times and foot_size; asynchronous on `stream`. */
+  void closedLoopBatch(int64_t n, int K, const double * foot0, const double * foot_pos, const int32_t * foot_id,
+                       const double * swing_start, const double * swing_end, const double * foot_size,
+                       const int32_t * num_knots, const double * knot_time, const double * knot_zmp, double * com_state,
+                       double * planned_zmp, double t0, double sim_dt, int cycles,
+                       const std::vector<double> & disturb_times = {}, double disturb_impulse = 0.0, bool warm_start = true,
+                       int32_t * status = nullptr, int32_t * violations = nullptr, double * traj_com = nullptr,
+                       double * traj_zmp = nullptr, void * stream = nullptr)
+  {
+    check(ccc_ism_closed_loop_device(handle_.get(), n, K, foot0, foot_pos, foot_id, swing_start, swing_end, foot_size,
+                                     num_knots, knot_time, knot_zmp, com_state, planned_zmp, t0, sim_dt, cycles,
+                                     static_cast<int>(disturb_times.size()), disturb_times.data(), disturb_impulse,
+                                     warm_start ? 1 : 0, status, violations, traj_com, traj_zmp, stream));
+  }
+
   /** \brief Number of steps in horizon (IntrinsicallyStableMpc1d::horizon_steps_). */
   int horizonSteps() const
   {

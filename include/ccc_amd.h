@@ -394,6 +394,46 @@ int ccc_ism_plan_batch_device(ccc_ism_t * h, int64_t n, const double * init, con
 int ccc_ism_plan_batch(ccc_ism_t * h, int64_t n, const double * init, const double * ref, double control_dt,
                        double * zmp, double * vel, int32_t * status);
 
+/* The control loop of tests/src/TestIntrinsicallyStableMpc.cpp:55-100 for n instances in ONE launch (csrc/ism_loop.hip):
+ * per cycle the references of the horizon are sampled from the instance's footstep timeline (zmpLimits,
+ * tests/src/FootstepManager.h:242-254) and reference-ZMP polyline (refZmp, :228-237; makeIntrinsicallyStableMpcRefData,
+ * :370-380), capture_point = pos + sqrt(h / g) vel (:67), planOnce(.., t, sim_dt), ComZmpSim2d::update
+ * (tests/src/SimModels.h:11-41), t += sim_dt, addDisturb.  One wavefront runs one axis of one instance through all the
+ * cycles; with warm_start != 0 the QP of a cycle starts from the solution, clamped set and multiplier of the one before.
+ *
+ *   K, foot0 .. foot_size     the footstep timeline, layout of ccc_zmp_closed_loop_device; K <= 16
+ *   num_knots [n] i32, knot_time [n][32], knot_zmp [n][32][2]   the polyline, layout of ccc_pvz_plan_knots_batch_device;
+ *                             1 .. CCC_PVZ_MAX_KNOTS knots, ascending; constant before the first and after the last knot
+ *                             (the convention of ccc_ddpzmp_closed_loop_device)
+ *   com_state   [n][2 axes][2]  f64  in / out: (pos, vel) of the simulated CoM
+ *   planned_zmp [n][2]          f64  in / out: the ZMP planned last (InitialParam::planned_zmp of the next plan)
+ *   t0, sim_dt, cycles               time of the first cycle, simulator step = control_dt, number of cycles
+ *   disturb_times [n_disturb <= 8]   HOST: at the first match times[d] <= t < times[d] + sim_dt (t after the step)
+ *                                    `disturb_impulse` is added to BOTH axes' velocity (SimModels.h:125-129, reference quirk)
+ *   status      [n][2]  i32  optional, per axis: (tridiagonal solves of all cycles << 8) | CCC_STATUS_SOLVED, or
+ *                            (cycle << 8) | CCC_STATUS_INFEASIBLE / CCC_STATUS_MAX_ITER for an axis that stopped at `cycle`:
+ *                            INFEASIBLE when the capture point cannot be caught inside the limits (decided in closed form
+ *                            before iterating: at'lo <= c <= at'hi and no lo_i > hi_i), MAX_ITER when a feasible QP used up
+ *                            its iteration budget.  A stopped axis keeps the state it entered that cycle with; the other
+ *                            axis and the other instances go on
+ *   violations  [n]     i32  optional, INCREMENTED by the number of (cycle, axis) pairs whose planned ZMP lies outside
+ *                            zmpLimits(t) (:84-85)
+ *   traj_com, traj_zmp [cycles][n][2]  f64  optional: CoM position before the step and planned ZMP of every cycle; NaN
+ *                            from the cycle on at which the axis stopped
+ * All DEVICE pointers but disturb_times and foot_size; asynchronous on `stream`, no allocation, graph-capturable.
+ * CCC_ERR_UNSUPPORTED for a handle of horizon_steps > 127 (the tridiagonal kernel's limit) and for K > 16 (what the LDS
+ * slice of a wavefront holds); CCC_ERR_INVALID_ARGUMENT for NULL required pointers, cycles < 0, sim_dt <= 0, n_disturb
+ * outside 0 .. 8.  num_knots lives on the device, so the call cannot see it: an instance whose count lies outside
+ * 1 .. CCC_PVZ_MAX_KNOTS stops at cycle 0 with CCC_STATUS_INFEASIBLE on both axes (the host-side packer of the Python
+ * mirror refuses such a polyline with CCC_ERR_UNSUPPORTED).  cycles = 0 leaves everything untouched. */
+int ccc_ism_closed_loop_device(ccc_ism_t * h, int64_t n, int K, const double * foot0, const double * foot_pos,
+                               const int32_t * foot_id, const double * swing_start, const double * swing_end,
+                               const double * foot_size, const int32_t * num_knots, const double * knot_time,
+                               const double * knot_zmp, double * com_state, double * planned_zmp, double t0, double sim_dt,
+                               int cycles, int n_disturb, const double * disturb_times, double disturb_impulse,
+                               int warm_start, int32_t * status, int32_t * violations, double * traj_com,
+                               double * traj_zmp, void * stream);
+
 /* ============================================================================================
  * CCC::LinearMpcZ   (/root/reference/include/CCC/LinearMpcZ.h:14-179)
  * the vertical companion of LinearMpcXY (it plans the total_force_z LinearMpcXY consumes).

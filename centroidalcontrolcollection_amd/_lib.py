@@ -111,6 +111,7 @@ ABI_SYMBOLS = [
     "ccc_step_destroy",
     "ccc_step_plan_batch_device",
     "ccc_step_plan_batch",
+    "ccc_step_closed_loop_device",
     "ccc_pvz_create",
     "ccc_pvz_destroy",
     "ccc_pvz_horizon_steps",

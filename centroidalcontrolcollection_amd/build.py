@@ -32,7 +32,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wal
 # the flags of the older units are part of their profiles' hashes and stay what they were)
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 UNIT_FLAGS = {"wrench_dist.hip": _NO_PACKED_FP32, "step_mpc.hip": _NO_PACKED_FP32,
-              "preview_zmp.hip": _NO_PACKED_FP32}
+              "preview_zmp.hip": _NO_PACKED_FP32, "step_mpc_loop.hip": _NO_PACKED_FP32}
 
 
 HASH_PATH = LIB_PATH + ".srchash"

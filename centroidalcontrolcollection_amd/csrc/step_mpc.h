@@ -20,6 +20,8 @@
 // no divergent loop bounds.  The ZMP rows are diagonal and go first: they ARE the initial R and d.  No LDS, no scratch.
 #pragma once
 
+#include <cstdint>
+
 #include "wave_group.h"
 
 namespace ccc_amd
@@ -191,4 +193,21 @@ __device__ __forceinline__ void step_backsub(const double (&Rc)[16], double dx, 
   }
   if constexpr(K > 0) step_backsub<K - 1>(Rc, dx, dy, ux, uy, lane);
 }
+
+template<int I>
+__device__ __forceinline__ void step_all_stages(const StepParams & P, StepRow & S, double (&Rc)[16], double & dx, double & dy)
+{
+  if constexpr(I > 0) step_all_stages<I - 1>(P, S, Rc, dx, dy);
+  step_stage<I>(P, S, Rc, dx, dy);
+}
 } // namespace ccc_amd
+
+// the handle of the C-ABI (csrc/step_mpc.hip creates it, csrc/step_mpc_loop.hip reads P and device)
+struct ccc_step
+{
+  int device = 0;
+  ccc_amd::StepParams P;
+  char * d_stage = nullptr;
+  int64_t cap = 0;
+  hipStream_t stream = nullptr;
+};

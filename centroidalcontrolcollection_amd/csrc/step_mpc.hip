@@ -12,13 +12,6 @@ namespace
 {
 constexpr double kStepG = 9.80665; // include/CCC/Constants.h:10
 
-template<int I>
-__device__ __forceinline__ void step_all_stages(const StepParams & P, StepRow & S, double (&Rc)[16], double & dx, double & dy)
-{
-  if constexpr(I > 0) step_all_stages<I - 1>(P, S, Rc, dx, dy);
-  step_stage<I>(P, S, Rc, dx, dy);
-}
-
 // 256 threads = four wavefronts = sixteen instances per workgroup.
 __global__ __launch_bounds__(256) void step_mpc_kernel(StepParams P, long n_inst, const int * __restrict__ num_elements,
                                                        const int * __restrict__ is_single_support,
@@ -126,15 +119,6 @@ __global__ __launch_bounds__(256) void step_mpc_kernel(StepParams P, long n_inst
 } // namespace ccc_amd
 
 using namespace ccc_amd;
-
-struct ccc_step
-{
-  int device = 0;
-  StepParams P;
-  char * d_stage = nullptr;
-  int64_t cap = 0;
-  hipStream_t stream = nullptr;
-};
 
 extern "C" int ccc_step_create(double com_height, const ccc_step_weights_t * weights, int device, ccc_step_t ** out)
 {

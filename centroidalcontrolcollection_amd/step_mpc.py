@@ -20,6 +20,17 @@ class _Weights(ctypes.Structure):
                                                "capture_point_rel")]
 
 
+class LoopParams(ctypes.Structure):
+    """ccc_step_loop_params_t: the constants of makeStepMpcRefData (FootstepManager.h:392-393) and of the footstep update
+    (TestStepMpc.cpp:100-105)."""
+    _fields_ = [("horizon_duration", ctypes.c_double), ("constant_zmp_duration", ctypes.c_double),
+                ("pre_duration", ctypes.c_double), ("enable_footstep_update", ctypes.c_int32)]
+
+    def __init__(self, horizon_duration=3.0, constant_zmp_duration=0.2, pre_duration=0.1, enable_footstep_update=True):
+        super().__init__(float(horizon_duration), float(constant_zmp_duration), float(pre_duration),
+                         int(bool(enable_footstep_update)))
+
+
 def _bind(L):
     if getattr(L, "_step_bound", False):
         return
@@ -32,6 +43,9 @@ def _bind(L):
     L.ccc_step_plan_batch_device.argtypes = [vp, ctypes.c_int64] + [vp] * 10
     L.ccc_step_plan_batch.restype = ctypes.c_int
     L.ccc_step_plan_batch.argtypes = [vp, ctypes.c_int64] + [vp] * 9
+    L.ccc_step_closed_loop_device.restype = ctypes.c_int
+    L.ccc_step_closed_loop_device.argtypes = [vp, ctypes.c_int64, ctypes.c_int] + [vp] * 7 + [
+        ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, vp, ctypes.c_double] + [vp] * 7
     L._step_bound = True
 
 
@@ -104,6 +118,34 @@ class StepMpc:
         _lib.check(self._L.ccc_step_plan_batch_device(self._h, num_elements.shape[0], p(num_elements), p(is_single_support),
                                                       p(end_time), p(zmp), p(x0), p(current_time), p(current_zmp),
                                                       p(next_foot_zmp), p(status), ctypes.c_void_p(stream.cuda_stream)))
+
+    def closed_loop_device(self, timeline, com_state, t0, sim_dt, cycles, disturb_times=(), impulse=0.0, params=None,
+                           status=None, updates=None, traj_com=None, traj_zmp=None, traj_next_foot=None, stream=None):
+        """ccc_step_closed_loop_device: `cycles` control cycles of TestStepMpc.cpp:55-116 for every instance in one launch.
+        timeline: dict of contiguous CUDA tensors (foot0 [n,2,2], foot_pos [n,K,2], foot_id [n,K] i32, swing_start /
+        swing_end / transit_end [n,K]); foot_pos is rewritten where the loop adapts a footstep.  com_state [n,2,2] is
+        updated in place; params a LoopParams (None: the reference's constants); status [n] i32, updates [n] i32
+        (incremented), traj_com / traj_zmp / traj_next_foot [cycles,n,2] are optional.  Returns the time after the last
+        cycle."""
+        import torch
+
+        n, K = timeline["foot_id"].shape
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+
+        def p(t):
+            return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+        dts = (ctypes.c_double * max(1, len(disturb_times)))(*disturb_times)
+        _lib.check(self._L.ccc_step_closed_loop_device(
+            self._h, n, K, *(p(timeline[k]) for k in ("foot0", "foot_pos", "foot_id", "swing_start", "swing_end",
+                                                      "transit_end")), p(com_state), float(t0), float(sim_dt), int(cycles),
+            len(disturb_times), dts, float(impulse), None if params is None else ctypes.cast(ctypes.byref(params), ctypes.c_void_p),
+            p(status), p(updates), p(traj_com), p(traj_zmp), p(traj_next_foot), ctypes.c_void_p(stream.cuda_stream)))
+        t = float(t0)
+        for _ in range(int(cycles)):
+            t += float(sim_dt)
+        return t
 
     def planOnce(self, ref_data, initial_param, current_time):
         """CCC::StepMpc::planOnce (src/StepMpc.cpp:202-247)."""

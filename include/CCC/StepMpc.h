@@ -225,6 +225,27 @@ public:
     return out;
   }
 
+  /** \brief The control loop of tests/src/TestStepMpc.cpp:55-116 for n instances in one launch (new): a thin forward to
+      ccc_step_closed_loop_device (ccc_amd.h), whose argument list and layouts it shares.  All pointers are device pointers
+      but disturb_times and params; asynchronous on `stream`. */
+  void closedLoopBatch(int64_t n, int K, const double * foot0, double * foot_pos, const int32_t * foot_id,
+                       const double * swing_start, const double * swing_end, const double * transit_end,
+                       double * com_state, double t0, double sim_dt, int cycles,
+                       const std::vector<double> & disturb_times = {}, double disturb_impulse = 0.0,
+                       const ccc_step_loop_params_t * params = nullptr, int32_t * status = nullptr,
+                       int32_t * updates = nullptr, double * traj_com = nullptr, double * traj_zmp = nullptr,
+                       double * traj_next_foot = nullptr, void * stream = nullptr)
+  {
+    if(ccc_step_closed_loop_device(mpc_1d_->handle(), n, K, foot0, foot_pos, foot_id, swing_start, swing_end, transit_end,
+                                   com_state, t0, sim_dt, cycles, static_cast<int>(disturb_times.size()),
+                                   disturb_times.data(), disturb_impulse, params, status, updates, traj_com, traj_zmp,
+                                   traj_next_foot, stream)
+       != CCC_OK)
+    {
+      throw std::runtime_error(std::string("[StepMpc] ") + ccc_last_error_string());
+    }
+  }
+
   /** \brief Status of the last call, one per instance: CCC_STATUS_* | CCC_STEP_HAS_NEXT_FOOT (new). */
   const std::vector<int32_t> & lastStatuses() const
   {

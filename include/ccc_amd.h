@@ -660,8 +660,50 @@ int ccc_step_plan_batch(ccc_step_t * h, int64_t n, const int32_t * num_elements,
                         const double * end_time, const double * zmp, const double * x0, const double * current_time,
                         double * current_zmp, double * next_foot_zmp, int32_t * status);
 
+/* The control loop of tests/src/TestStepMpc.cpp:55-116 for n instances, `cycles` cycles, in ONE launch
+ * (csrc/step_mpc_loop.hip).  Per cycle: FootstepManager::update(t) (tests/src/FootstepManager.h:147-160: the front
+ * footstep's position becomes the stance of its foot once swing_end <= t, then footsteps are popped while transit_end < t),
+ * makeStepMpcRefData(t) (:385-448, built at t - 1e-6), planOnce(.., t), ComZmpSim2d::update (tests/src/SimModels.h:11-41),
+ * t += sim_dt, addDisturb, and the footstep update of :99-115: when the list is not empty, front.swing_end - pre_duration
+ * <= t < front.swing_end - pre_duration + sim_dt and the plan has a next foot, the front footstep moves to next_foot_zmp.
+ * One instance per 16-lane row keeps its footstep list, footstance and CoM state in registers through all the cycles.
+ *
+ *   K, foot0, foot_id, swing_start, swing_end   the footstep timeline, layout of ccc_zmp_closed_loop_device; K <= 16
+ *   foot_pos    [n][K][2]       f64  in / out: the landing positions; the loop rewrites those it adapts
+ *   transit_end [n][K]          f64  end of the double support after the swing (Footstep::transit_end_time)
+ *   com_state   [n][2 axes][2]  f64  in / out: (pos, vel) of the simulated CoM
+ *   t0, sim_dt, cycles               time of the first cycle, simulator step, number of cycles
+ *   disturb_times [n_disturb <= 8]   HOST: at the first match times[d] <= t < times[d] + sim_dt (t after the step)
+ *                                    `disturb_impulse` is added to BOTH axes' velocity (SimModels.h:125-129, reference quirk)
+ *   params                           HOST, NULL = the constants of the reference {3.0, 0.2, 0.1, 1}
+ *   status      [n]     i32  optional: CCC_STATUS_SOLVED, or (cycle << 8) | CCC_STATUS_INFEASIBLE for an instance whose
+ *                            element list could not be planned at `cycle`: more than CCC_STEP_MAX_ELEMENTS elements inside
+ *                            the horizon, a duration <= 0 (planOnce gets t, the list is built at t - 1e-6: the first
+ *                            duration may lie in (-1e-6, 0] and is planned as it stands, as the reference does; it is
+ *                            refused from -2e-6 down) or two consecutive double supports.  Such an instance keeps the
+ *                            com_state and foot_pos it entered that cycle with; the other instances go on
+ *   updates     [n]     i32  optional, INCREMENTED once per footstep update applied
+ *   traj_com, traj_zmp, traj_next_foot [cycles][n][2]  f64  optional: CoM position before the step, current_zmp and
+ *                            next_foot_zmp of every cycle (NaN where the plan had no next foot); all NaN from the cycle on
+ *                            at which the instance stopped
+ * All DEVICE pointers but disturb_times and params; asynchronous on `stream`, no allocation, graph-capturable.
+ * CCC_ERR_UNSUPPORTED for K > 16 (one footstep per lane of the row); CCC_ERR_INVALID_ARGUMENT for NULL required pointers,
+ * cycles < 0, sim_dt <= 0, n_disturb outside 0 .. 8 or a duration in params <= 0.  cycles = 0 leaves everything
+ * untouched. */
+typedef struct
+{
+  double horizon_duration, constant_zmp_duration, pre_duration;
+  int32_t enable_footstep_update;
+} ccc_step_loop_params_t;
+int ccc_step_closed_loop_device(ccc_step_t * h, int64_t n, int K, const double * foot0, double * foot_pos,
+                                const int32_t * foot_id, const double * swing_start, const double * swing_end,
+                                const double * transit_end, double * com_state, double t0, double sim_dt, int cycles,
+                                int n_disturb, const double * disturb_times, double disturb_impulse,
+                                const ccc_step_loop_params_t * params, int32_t * status, int32_t * updates,
+                                double * traj_com, double * traj_zmp, double * traj_next_foot, void * stream);
+
 /* ============================================================================================
- * CCC::PreviewControlZmp   (/root/reference/include/CCC/PreviewControlZmp.h:92-140, src/PreviewControlZmp.cpp:15-76)
+ * CCC::PreviewControlZmp  (/root/reference/include/CCC/PreviewControlZmp.h:92-140, src/PreviewControlZmp.cpp:15-76)
  * CCC::SingularPreviewControlZmp   (include/CCC/SingularPreviewControlZmp.h:86-130, src/SingularPreviewControlZmp.cpp:7-88)
  * -- csrc/preview_zmp.hip.  Both are, per axis, u = -K x + sum_{i<N} w_i r_i with r_i = ref_zmp_func(current_time +
  * (i + off) horizon_dt) and a short epilogue; one handle type serves both, `kind` selects K, w, off and the epilogue:

@@ -30,6 +30,7 @@
 #include "sym_tableau.h"
 #include "wave_group.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -1157,6 +1158,106 @@ __global__ __launch_bounds__((SymTab<NP, TS, TPT>::NT), (SymTab<NP, TS, TPT>::kM
 // ---------------------------------------------------------------------------------------------
 namespace ccc_amd
 {
+// The second half of a counting sort whose first half ran inside the caller's own kernel (csrc/zmp.hip zmp_predict_kernel):
+// item i already knows its bucket (0 = first in the order) and its rank among the items of that bucket, ranked[i] =
+// (bucket, rank), and total[b] holds the items of bucket b.  order[prefix(total)[bucket] + rank] = i, one launch.
+// `total`: kRankedTotalInts ints of the caller's that are ZERO before the first half runs; this launch leaves them zero
+// again (the workgroup that finishes last clears them), so no memset or clearing launch ever enters the stream.
+// *prepared: the caller's "the launch attributes are set on this device" flag.
+constexpr int kRankedBuckets = 16384;
+constexpr int kRankedTotalInts = kRankedBuckets + 32; // (the counts, then the ticket of the workgroups that are done)
+__device__ __forceinline__ int ranked_bucket(int t) { return kRankedBuckets - 1 - (t < 0 ? 0 : (t > kRankedBuckets - 1 ? kRankedBuckets - 1 : t)); }
+
+// The place pass of a sort whose counting half ran in the caller's kernel (above): every item carries its bucket and
+// its rank inside the bucket, so a workgroup needs the exclusive prefix of total[] over the buckets and nothing else --
+// 64 KB from L2, not a column block of a [chunks][buckets] table, which is what lets the key have 16384 buckets.  Thread t
+// scans the 64 buckets [64 t, 64 t + 64) in LDS; slot b of a 64-bucket segment is rotated by the segment's number, so that
+// both the coalesced fill (consecutive buckets) and the per-thread scan (stride 64) are free of bank conflicts.
+constexpr int kRankedPer = kRankedBuckets / 256;
+static_assert(kRankedPer == 64, "one 64-bucket segment per thread (ranked_slot, off[])");
+__device__ __forceinline__ int ranked_slot(int b) { return (b & ~63) | ((b + (b >> 6)) & 63); }
+
+__global__ __launch_bounds__(256) void order_place_ranked_kernel(const int2 * __restrict__ ranked, int n, int chunk, int * total,
+                                                                 int * __restrict__ order)
+{
+  extern __shared__ int ranked_lds[];
+  int * base = ranked_lds;            // [kRankedBuckets] items of the buckets before b inside b's segment
+  int * off = base + kRankedBuckets;  // [256]            items of the segments before
+  int * wsum = off + 256;             // [4]
+  int * last = wsum + 4;
+  const int tid = threadIdx.x;
+  const int lo = blockIdx.x * chunk, hi = lo + chunk < n ? lo + chunk : n;
+  // (everything this thread reads from memory is asked for at once: the counts, and its first four items)
+  int c[kRankedPer];
+#pragma unroll
+  for(int k = 0; k < kRankedPer; k++) c[k] = total[k * 256 + tid];
+  int2 r[4];
+#pragma unroll
+  for(int k = 0; k < 4; k++) r[k] = lo + tid + k * 256 < hi ? ranked[lo + tid + k * 256] : make_int2(0, 0);
+#pragma unroll
+  for(int k = 0; k < kRankedPer; k++) base[ranked_slot(k * 256 + tid)] = c[k];
+  __syncthreads();
+  // (every count this workgroup reads has arrived.  The workgroup that draws the last ticket knows that all the others are
+  //  done with total[] as well, and leaves it zero for the next call; the ticket is drawn here and looked at at the end)
+  int ticket = 0;
+  if(tid == 192) ticket = atomicAdd(total + kRankedBuckets, 1);
+  int sum = 0;
+  for(int j0 = 0; j0 < kRankedPer; j0 += 16) // (reads before writes, sixteen at a time: LDS accesses that may alias serialise)
+  {
+    int v[16];
+#pragma unroll
+    for(int k = 0; k < 16; k++) v[k] = base[ranked_slot(tid * kRankedPer + j0 + k)];
+#pragma unroll
+    for(int k = 0; k < 16; k++)
+    {
+      base[ranked_slot(tid * kRankedPer + j0 + k)] = sum;
+      sum += v[k];
+    }
+  }
+  int incl = sum;
+  for(int d = 1; d < 64; d <<= 1)
+  {
+    const int o = __shfl_up(incl, d);
+    if((tid & 63) >= d) incl += o;
+  }
+  if((tid & 63) == 63) wsum[tid >> 6] = incl;
+  __syncthreads();
+  int before = 0;
+  for(int w = 0; w < (tid >> 6); ++w) before += wsum[w];
+  off[tid] = before + incl - sum;
+  __syncthreads();
+  auto place = [&](int2 q, int i) {
+    const int b = q.x & (kRankedBuckets - 1);
+    const int p = base[ranked_slot(b)] + off[b >> 6] + q.y;
+    if((unsigned)p < (unsigned)n) order[p] = i; // (a permutation whenever total[] was clean; never out of bounds)
+  };
+#pragma unroll
+  for(int k = 0; k < 4; k++)
+    if(lo + tid + k * 256 < hi) place(r[k], lo + tid + k * 256);
+  for(int i = lo + tid + 4 * 256; i < hi; i += 256) place(ranked[i], i);
+  if(tid == 192) *last = ticket == (int)gridDim.x - 1;
+  __syncthreads();
+  if(*last)
+    for(int k = tid; k < kRankedTotalInts; k += 256) total[k] = 0;
+}
+
+int order_place_ranked(const int2 * ranked, int n, int * order, int * total, bool * prepared, void * stream)
+{
+  const size_t lds = (size_t)(kRankedBuckets + 256 + 8) * sizeof(int);
+  if(!*prepared)
+  {
+    CCC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&order_place_ranked_kernel),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    *prepared = true;
+  }
+  const int blocks = std::max(1, std::min(kOrderBlocks, (n + 1023) / 1024));
+  const int chunk = (n + blocks - 1) / blocks;
+  hipLaunchKernelGGL(order_place_ranked_kernel, dim3(blocks), dim3(256), lds, reinterpret_cast<hipStream_t>(stream), ranked, n,
+                     chunk, total, order);
+  if(hipGetLastError() != hipSuccess) return fail(CCC_ERR_HIP, "order_place_ranked: launch failed");
+  return CCC_OK;
+}
+
 template<int WAVES>
 __global__ __launch_bounds__(WAVES * 64) void zmp_predict_kernel(ZmpDev P, long nqp, const double * __restrict__ x0,
                                                                  const double * __restrict__ zlim, int * __restrict__ pred)
@@ -1174,6 +1275,84 @@ __global__ __launch_bounds__(WAVES * 64) void zmp_predict_kernel(ZmpDev P, long 
   }
   for(int d = 16; d >= 1; d >>= 1) k += __shfl_xor(k, d, 32);
   if(li == 0 && qp < nqp) pred[qp] = (int)(k + 0.5f); // (<= 16 / (1 - exp(-dt / tau)): inside order_by_count's 256 buckets)
+}
+
+// From kRankedMinQp QPs (the headline's 131072) the same key is sorted on 16384 buckets, in two launches instead of three.
+// What separates the 1.18 of the 256-bucket key from the 1.14 of the key sorted as it is are the QPs that
+// violate the SAME rows -- 131072 QPs of the bench workload show some 12600 distinct violation patterns, and two QPs of one
+// pattern are the best pair there is; in the numpy model (tests/tools/zmp_schedule_key.py) a window of 64 neighbours
+// shuffled loses most of the difference, and equal-width buckets only get there when they tell the patterns apart: 1.165 at
+// 1024 buckets, 1.155 at 4096, 1.148 at 16384 (kRankedBuckets).  A [chunks][buckets] table cannot be that wide -- every
+// place workgroup reads a column block of it -- so the count is done here, where every key is in a register anyway: a
+// workgroup counts its chunk in LDS (which also ranks every QP inside its (chunk, bucket) cell), then claims a range of
+// each bucket it met with ONE atomic on total[bucket] per cell; what the atomic returns is the cell's offset inside the
+// bucket.  Every QP leaves with (bucket, rank inside the bucket); the place pass (order_place_ranked above) needs the
+// prefix of total[] and nothing else.  Within a bucket the order is whatever the atomics give, as before.
+// scale: the largest possible key, 1 / (1 - exp(-dt / tau)), maps to the last bucket (per handle, build_model).
+// What it costs: with buckets this fine nearly every QP is a cell of its own, i.e. one returning device-scope atomic per
+// QP.  Measured on an MI355X: 131072 QPs, 22.4 + 9.3 us against the 19.0 + 4.8 + 9.3 us of the
+// three launches, and the solve 10 us shorter for the pairs; 16384 QPs, 10.5 + 8.0 us against 4.6 + 4.8 + 5.2 us with no
+// shorter solve to show for it -- hence the threshold, below which the three launches stay.
+constexpr int64_t kRankedMinQp = 131072;
+constexpr int kPredWaves = 16;    // 32 QPs per pass of a workgroup
+constexpr int kPredPasses = 8;     // ... and eight passes: a chunk is 256 QPs
+template<int WAVES>
+__global__ __launch_bounds__(WAVES * 64) void zmp_predict_rank_kernel(ZmpDev P, long nqp, float decay, float scale,
+                                                                      const double * __restrict__ x0,
+                                                                      const double * __restrict__ zlim, int2 * __restrict__ pred,
+                                                                      int * total)
+{
+  extern __shared__ int pred_cnt[];                             // [kRankedBuckets]
+  __shared__ int bkt[kPredPasses * WAVES * 2], rnk[kPredPasses * WAVES * 2]; // per QP of the chunk
+  const int tid = threadIdx.x, lane = tid & 63, li = lane & 31, grp = tid >> 5;
+  const int N = P.N;
+  constexpr int len = kPredPasses * WAVES * 2;
+  const long first = (long)blockIdx.x * len;
+  const bool row = li < N;
+  const double a0 = row ? P.A[li * 3 + 0] : 0.0, a1 = row ? P.A[li * 3 + 1] : 0.0, a2 = row ? P.A[li * 3 + 2] : 0.0;
+  const float w = row ? __expf(-(float)li * decay) : 0.0f; // (rows beyond the horizon add nothing)
+  // the keys of all passes first -- every load of the chunk in flight at once -- and the counters cleared under them
+  float key[kPredPasses];
+#pragma unroll
+  for(int ps = 0; ps < kPredPasses; ++ps)
+  {
+    const long qp = first + ps * WAVES * 2 + grp;
+    float k = 0.0f;
+    if(qp < nqp && row)
+    {
+      const double fr = a0 * x0[qp * 3 + 0] + a1 * x0[qp * 3 + 1] + a2 * x0[qp * 3 + 2];
+      const double lo = zlim[qp * 2 * N + li] - fr, hi = zlim[qp * 2 * N + N + li] - fr;
+      if(lo > 0.0 || hi < 0.0) k = w;
+    }
+    key[ps] = k;
+  }
+  for(int k = tid; k < kRankedBuckets; k += WAVES * 64) pred_cnt[k] = 0;
+  __syncthreads();
+#pragma unroll
+  for(int ps = 0; ps < kPredPasses; ++ps)
+  {
+    const int q = ps * WAVES * 2 + grp;
+    const long qp = first + q;
+    float k = key[ps];
+    for(int d = 16; d >= 1; d >>= 1) k += __shfl_xor(k, d, 32);
+    if(li == 0 && qp < nqp)
+    {
+      const int b = ranked_bucket((int)(k * scale + 0.5f));
+      bkt[q] = b;
+      rnk[q] = atomicAdd(&pred_cnt[b], 1);
+    }
+  }
+  __syncthreads();
+  // the first QP of every cell claims the cell's range of its bucket and leaves the range's start in the counter's place
+  for(int q = tid; q < len; q += WAVES * 64)
+    if(first + q < nqp && rnk[q] == 0)
+    {
+      const int b = bkt[q];
+      pred_cnt[b] = atomicAdd(&total[b], pred_cnt[b]);
+    }
+  __syncthreads();
+  for(int q = tid; q < len; q += WAVES * 64)
+    if(first + q < nqp) pred[first + q] = make_int2(bkt[q], pred_cnt[bkt[q]] + rnk[q]);
 }
 } // namespace ccc_amd
 
@@ -1195,7 +1374,11 @@ struct ccc_zmp
   int * order_scratch = nullptr;         // (order_by_count's table)
   int * diff = nullptr;                  // |trips - trips of the call before| per QP, and the verdict it leads to:
   int *trust_host = nullptr, *trust_dev = nullptr; // page-locked host memory, read without waiting (0: do not follow)
-  int * pred = nullptr;                  // predicted trips per QP of THIS call (zmp_predict_kernel), when no history is followed
+  int * pred = nullptr;                  // predicted trips per QP of THIS call (zmp_predict_kernel), when no history is followed;
+                                         // from kRankedMinQp QPs an int2 each: the key's bucket and the QP's rank inside it
+  int * pred_total = nullptr;            // QPs per bucket of that key: zero between calls (order_place_ranked)
+  float pred_decay = 0, pred_scale = 0;  // the key's dt / tau and its buckets per unit (build_model)
+  bool attr_pred = false, attr_place = false;
   std::vector<void *> retired;           // scheduling buffers that were outgrown: kept until the handle goes, because a
                                          // hipGraph captured at the smaller size still holds their addresses
   int64_t hist_cap = 0, hist_n = -1;     // (hist_n: the QPs of the call the counts belong to, -1 = none yet)
@@ -1261,6 +1444,11 @@ void build_model(ccc_zmp * h)
   const int N = h->N;
   const double dt = h->horizon_dt, c2 = -1 * h->com_height / kG;
   h->c2 = c2;
+  // the predicted schedule's key, sum_i exp(-i dt / tau) over the violated rows, tau = 2.35 sqrt(h / g): no horizon reaches
+  // 1 / (1 - exp(-dt / tau)), which goes to the last bucket
+  const double decay = dt / (2.35 * std::sqrt(-c2));
+  h->pred_decay = (float)decay;
+  h->pred_scale = (float)((kRankedBuckets - 1) * (1.0 - std::exp(-decay)));
   h->A_seq.assign((size_t)N * 3, 0.0);
   h->B_seq.assign((size_t)N * N, 0.0);
   std::vector<double> b(N);
@@ -1342,18 +1530,25 @@ int launch(ccc_zmp * h, int64_t n, const double * x0, const double * zlim, doubl
   {
     // (the outgrown buffers are RETIRED, not freed: a hipGraph captured at the smaller size replays launches that read and
     //  write them -- ADVICE r5: freed, that was silent corruption; they go with the handle)
-    for(int * q : {h->hist, h->order, h->diff, h->pred})
+    for(void * q : {(void *)h->hist, (void *)h->order, (void *)h->diff, (void *)h->pred})
       if(q) h->retired.push_back(q);
     // (capacity grows by at least half, so that a caller whose batches creep upwards retires a geometric series of
     //  buffers -- at most twice the final size in all -- not one set per call)
     const int64_t cap = std::max<int64_t>(nqp, h->hist_cap + h->hist_cap / 2);
-    h->hist = h->order = h->diff = h->pred = nullptr;
+    h->hist = h->order = h->diff = nullptr;
+    h->pred = nullptr;
     h->hist_cap = 0;
     h->hist_n = -1;
     CCC_HIP_CHECK(hipMalloc(&h->hist, (size_t)cap * sizeof(int)));
     CCC_HIP_CHECK(hipMalloc(&h->order, (size_t)cap * sizeof(int)));
     CCC_HIP_CHECK(hipMalloc(&h->diff, (size_t)cap * sizeof(int)));
-    CCC_HIP_CHECK(hipMalloc(&h->pred, (size_t)cap * sizeof(int)));
+    CCC_HIP_CHECK(hipMalloc(&h->pred, (size_t)cap * sizeof(int2)));
+    if(!h->pred_total)
+    {
+      // (cleared once, here, where no capture can be active; from then on every place pass leaves it clear)
+      CCC_HIP_CHECK(hipMalloc(&h->pred_total, (size_t)kRankedTotalInts * sizeof(int)));
+      CCC_HIP_CHECK(hipMemset(h->pred_total, 0, (size_t)kRankedTotalInts * sizeof(int)));
+    }
     if(!h->order_scratch) CCC_HIP_CHECK(hipMalloc(&h->order_scratch, (size_t)kOrderScratchInts * sizeof(int)));
     if(!h->trust_host)
     {
@@ -1438,11 +1633,29 @@ int launch(ccc_zmp * h, int64_t n, const double * x0, const double * zlim, doubl
   // the schedule of this call from a prediction of every QP's trips (no history followed) ...
   if(predicted)
   {
-    constexpr int PW = 4;
-    hipLaunchKernelGGL((zmp_predict_kernel<PW>), dim3((unsigned)((nqp + 2 * PW - 1) / (2 * PW))), dim3(PW * 64), 0, stream, P,
-                       (long)nqp, x0, zlim, h->pred);
-    if(int orc = order_by_count(h->pred, (int)nqp, h->order, h->order_scratch, nullptr, 0, nullptr, stream, nullptr, nullptr))
-      return orc;
+    if(nqp >= kRankedMinQp)
+    {
+      constexpr int PW = kPredWaves, len = kPredPasses * 2 * PW;
+      const size_t plds = (size_t)kRankedBuckets * sizeof(int);
+      if(!h->attr_pred)
+      {
+        CCC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&zmp_predict_rank_kernel<PW>),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)plds));
+        h->attr_pred = true;
+      }
+      hipLaunchKernelGGL((zmp_predict_rank_kernel<PW>), dim3((unsigned)((nqp + len - 1) / len)), dim3(PW * 64), plds, stream, P,
+                         (long)nqp, h->pred_decay, h->pred_scale, x0, zlim, reinterpret_cast<int2 *>(h->pred), h->pred_total);
+      if(int orc = order_place_ranked(reinterpret_cast<int2 *>(h->pred), (int)nqp, h->order, h->pred_total, &h->attr_place, stream))
+        return orc;
+    }
+    else
+    {
+      constexpr int PW = 4;
+      hipLaunchKernelGGL((zmp_predict_kernel<PW>), dim3((unsigned)((nqp + 2 * PW - 1) / (2 * PW))), dim3(PW * 64), 0, stream, P,
+                         (long)nqp, x0, zlim, h->pred);
+      if(int orc = order_by_count(h->pred, (int)nqp, h->order, h->order_scratch, nullptr, 0, nullptr, stream, nullptr, nullptr))
+        return orc;
+    }
     P.order = h->order;
   }
   // ... or from the pivot counts of the last one: a counting sort, longest first (common.hip)
@@ -1800,6 +2013,7 @@ extern "C" void ccc_zmp_destroy(ccc_zmp_t * h)
   if(h->order_scratch) (void)hipFree(h->order_scratch);
   if(h->diff) (void)hipFree(h->diff);
   if(h->pred) (void)hipFree(h->pred);
+  if(h->pred_total) (void)hipFree(h->pred_total);
   for(void * q : h->retired) (void)hipFree(q);
   if(h->trust_host) (void)hipHostFree(h->trust_host);
   if(h->dG) (void)hipFree(h->dG);
